@@ -1,6 +1,6 @@
 """Benchmark: batched 12-var contact-force QP solves/s on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 Workload = BASELINE.json configs[1]: a batch of 1 024 identical-sparsity C1
 contact-force QPs (12 vars / 20 ineq / 6 eq) per GPU.  One step =
@@ -12,7 +12,12 @@ Shards are independent (weak scaling): rank r owns QP ids [r*B, (r+1)*B);
 config 5 (65 536 QPs over 8 GPUs) is `--gpus 8 --batch 8192`.
 
 At this batch size qpb_solve runs the row kernel (four QPs per wavefront).
-Beside the headline, rank 0 of a 1-GPU run also measures a 2^20-QP batch
+A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`); --dump-outputs DIR also writes the last timed step's
+outputs (dump_outputs).  Everything else is behind --full: the headline's
+kernel duration (HIP events around further launches) with the roofline and
+FP64 figures and solve statistics derived from it, and the secondary legs:
+beside the headline, rank 0 of a 1-GPU run also measures a 2^20-QP batch
 (working set ~2 GB, far above the 256 MB Infinity Cache) as `large_batch`, the
 HBM-scale throughput figure; configs[2] (4 gait patterns, 4 streams) as
 `mixed_patterns`; and under `shapes` configs[3] (MPC horizon, N = 380, tree
@@ -44,16 +49,21 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1024, help="QPs per GPU per step (configs[1]: 1024)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its kernel duration, roofline and FP64 figures and solve "
+                         "statistics, and (1-GPU runs) the large-batch, configs[2], shape and CPU-baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--large-batch", type=int, default=1 << 20,
-                    help="QPs of the secondary large-batch leg (1-GPU runs; 0 = skip)")
+                    help="--full: QPs of the secondary large-batch leg (1-GPU runs; 0 = skip)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "lane", "wave", "wave1", "auto1"])
     ap.add_argument("--no-mixed", dest="mixed", action="store_false",
-                    help="skip the configs[2] leg (4 gait patterns x 1024 QPs)")
+                    help="--full: skip the configs[2] leg (4 gait patterns x 1024 QPs)")
     ap.add_argument("--no-shapes", dest="shapes", action="store_false",
-                    help="skip the configs[3] (MPC) and controller-shape legs")
+                    help="--full: skip the configs[3] (MPC) and controller-shape legs")
     ap.add_argument("--tol", type=float, default=1e-6)
     ap.add_argument("--exact", action="store_true", help="bench the bit-faithful kernel")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline legs")
     ap.add_argument("--cpu-sample", type=int, default=65536)
     ap.add_argument("--cpu-passes", type=int, default=10)
     ap.add_argument("--dry-run", action="store_true",
@@ -274,10 +284,38 @@ def shape_leg(name, gen, B, tol, dev, steps=50, warmup=5, cpu=None):
     return res
 
 
-def run_leg(plan, B, steps, warmup, tol, dev, rank, world, seed, gather=True, gen=None, info=None):
+def dump_outputs(dirname, plan, B, out, best, winner, rank, budget=60_000_000):
+    """--dump-outputs: what a caller of the timed step receives -- the solve's x, y, z,
+    s, fval, flag, iters and stats ([B, ...], untiled) and the argmin `best` = {fval,
+    index} (with the gather, also `winner` = {fval, global index, x*}) -- as float64
+    DIR/<name>.npy (rank r > 0 of a multi-GPU run: <name>.rank<r>.npy).  A batch whose
+    arrays exceed `budget` bytes is written as a fixed seeded sample of its QPs, whose
+    ids are `rows`."""
+    from apf_quadruped_amd.batch import from_tiled
+    os.makedirs(dirname, exist_ok=True)
+    widths = dict(x=plan.n, y=plan.p, z=plan.m, s=plan.m, stats=6)
+    # per QP: the rows above + fval, flag, iters and its id; per dump: best and winner
+    cap = (budget - 8 * (4 + plan.n)) // (8 * (sum(widths.values()) + 4))
+    rows = None if B <= cap else np.sort(np.random.default_rng(0).choice(B, cap, replace=False))
+    arrays = {k: from_tiled(out[k], B, w).cpu().numpy() for k, w in widths.items() if w}
+    arrays.update({k: out[k][:B].cpu().numpy() for k in ("fval", "flag", "iters")})
+    if rows is not None:
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows
+    arrays["best"] = best.cpu().numpy()
+    if winner is not None:
+        arrays["winner"] = winner.cpu().numpy()
+    suffix = f".rank{rank}.npy" if rank else ".npy"
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + suffix), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def run_leg(plan, B, steps, warmup, tol, dev, rank, world, seed, gather=True, gen=None, info=None,
+            kernel_events=True, dump=None):
     """Timed loop of `steps` steps (solve + argmin [+ all_gather]) on resident
     inputs.  Returns (wall seconds max over ranks, mean kernel ms max over
-    ranks, outputs, gathered winners); `info` (a dict) receives the gather path."""
+    ranks (None without kernel_events), outputs, gathered winners); `info` (a dict)
+    receives the gather path; `dump`: a directory for dump_outputs."""
     import torch
     import torch.distributed as dist
     from apf_quadruped_amd.shard import make_argmin_gather, shard_range
@@ -343,25 +381,29 @@ def run_leg(plan, B, steps, warmup, tol, dev, rank, world, seed, gather=True, ge
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # kernel duration: one HIP event pair on the launch stream around kev further
+    last = (steps - 1) % nbuf
+    if dump:
+        dump_outputs(dump, plan, B, outs[last], bests[last], winners[last] if coll else None, rank)
+    # kernel duration (kernel_events): one HIP event pair on the launch stream around kev further
     # back-to-back launches (GPU-bound: a launch is queued faster than the kernel
     # runs), so the average is the kernel plus the ~1 us dispatch gap -- an upper
     # bound that rocprof's per-dispatch durations (profiles/) bracket from below.
     # Per-launch event pairs would add their own ~3 us; per-step events inside the
     # timed loop cost ~8 us of host time per step, so they stay out of it.
-    kev = min(steps, 50)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for i in range(kev):
-        solves[0]()
-    e1.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = e0.elapsed_time(e1) / kev
+    kern_ms = None
+    if kernel_events:
+        kev = min(steps, 50)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for i in range(kev):
+            solves[0]()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = e0.elapsed_time(e1) / kev
     if world > 1:
-        t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed, kern_ms or 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, kern_ms = float(t[0]), float(t[1])
-    last = (steps - 1) % nbuf
+        elapsed, kern_ms = float(t[0]), float(t[1]) if kernel_events else None
     if coll:
         result = winners[last].clone()
         ag.close()
@@ -685,21 +727,25 @@ def main():
     B = args.batch
     ginfo = {}
     elapsed, kern_ms, out, gathered = run_leg(plan, B, args.steps, args.warmup, args.tol, dev, rank, world, seed,
-                                              info=ginfo)
+                                              info=ginfo, kernel_events=args.full, dump=args.dump_outputs)
     kname = plan.kernel_name(B)
-    flags = out["flag"].cpu().numpy()
-    iters = out["iters"].cpu().numpy()
-    mean_it = float(iters.mean())
     ms_step = elapsed * 1e3 / args.steps
     value = world * B * args.steps / elapsed
-    bpq = plan.bytes_per_qp()
-    achieved = bpq * B / (kern_ms * 1e-3) / 1e9
-    fpq = flops_per_qp(plan.info, mean_it)
-    fp64_tf = fpq * B / (kern_ms * 1e-3) / 1e12
+    # everything below the headline is --full: the headline's own kernel duration and
+    # solve statistics on every rank count, the secondary legs on rank 0 of a 1-GPU run
+    legs = args.full and rank == 0 and world == 1
+    if args.full:
+        flags = out["flag"].cpu().numpy()
+        iters = out["iters"].cpu().numpy()
+        mean_it = float(iters.mean())
+        bpq = plan.bytes_per_qp()
+        achieved = bpq * B / (kern_ms * 1e-3) / 1e9
+        fpq = flops_per_qp(plan.info, mean_it)
+        fp64_tf = fpq * B / (kern_ms * 1e-3) / 1e12
 
     # secondary leg: one large batch per launch (row kernel), HBM-scale numbers
     large = None
-    if rank == 0 and world == 1 and args.large_batch > 0:
+    if legs and args.large_batch > 0:
         BL = args.large_batch
         el, km, outl, _ = run_leg(plan, BL, 10, 2, args.tol, dev, 0, 1, seed, gather=False)
         kl = plan.kernel_name(BL)
@@ -718,17 +764,17 @@ def main():
     # configs[2]: 4 096 QPs across the 4 gait contact patterns (mixed KKT sparsity):
     # one plan per pattern, all four in one group launch
     mixed = None
-    if rank == 0 and world == 1 and args.mixed:
+    if legs and args.mixed:
         mixed = mixed_patterns_leg(args.tol, dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if legs and not args.no_cpu:
         cpu = cpu_baseline(seed, args.cpu_sample, args.cpu_passes, args.tol)
 
     # configs[3] (MPC horizon, N = 380, band kernel) and the controller's own
     # stance QP (30/68/18), each with its CPU reference
     shapes = None
-    if rank == 0 and world == 1 and args.shapes:
+    if legs and args.shapes:
         from apf_quadruped_amd import workloads as W
         shapes = [
             shape_leg("configs[3]: MPC horizon N=10 (120/200/60), batch 1024", lambda ids: W.mpc_qp(plans.SEED + 4, ids),
@@ -767,21 +813,25 @@ def main():
                        "qps_per_gpu": B, "global_batch": B * world, "tol": args.tol,
                        "kernel": kname, "arith": "exact" if args.exact else "fast",
                        "kkt_N": plan.info.N, "nnz_L": plan.info.lnz, "parallelism": f"shard{world}"},
-            "roofline": {"bound": measured_bound(kname, B), "roofline_ref": "hbm", "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_for(kname, B),
-                         "algorithmic_bytes_per_launch": bpq * B, "bytes_per_qp": bpq,
-                         "kernel_ms": kern_ms, "kernel": kname,
-                         "limiter": limiter_for(B) if kname.startswith("qpb_row") else None},
-            "fp64": dict({"achieved_tflops": fp64_tf, "peak_tflops": FP64_PEAK_TFLOPS,
-                          "frac": fp64_tf / FP64_PEAK_TFLOPS, "flops_per_qp": fpq}, **fp64_issued(kname, B)),
-            "mean_iters": mean_it,
-            "optimal_frac": float((flags == 0).mean()),
-            "large_batch": large,
-            "mixed_patterns": mixed,
-            "shapes": shapes,
-            "cpu_baseline": cpu,
+            "full": args.full,
         }
+        if args.full:
+            line.update({
+                "roofline": {"bound": measured_bound(kname, B), "roofline_ref": "hbm", "achieved": achieved,
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_for(kname, B),
+                             "algorithmic_bytes_per_launch": bpq * B, "bytes_per_qp": bpq,
+                             "kernel_ms": kern_ms, "kernel": kname,
+                             "limiter": limiter_for(B) if kname.startswith("qpb_row") else None},
+                "fp64": dict({"achieved_tflops": fp64_tf, "peak_tflops": FP64_PEAK_TFLOPS,
+                              "frac": fp64_tf / FP64_PEAK_TFLOPS, "flops_per_qp": fpq}, **fp64_issued(kname, B)),
+                "mean_iters": mean_it,
+                "optimal_frac": float((flags == 0).mean()),
+                "large_batch": large,
+                "mixed_patterns": mixed,
+                "shapes": shapes,
+                "cpu_baseline": cpu,
+            })
         if world > 1:
             g = gathered.cpu().numpy()          # {fval, global index, x*} from qpb_argmin_allgather
             gi = int(g[1])

@@ -8,11 +8,11 @@ IFS=';' read -ra VS <<< "${VARIANTS:--;QPB_DPP_NOP=0}"
 for rep in 1 2; do for v in "${VS[@]}"; do
   o="$v"; [ "$o" = "-" ] && o=""; ev=""
   case "$o" in env:*) ev="${o#env:}"; o="";; esac
-  env $ev QPB_WAVE_OPTS="$o" timeout -k 10 300 python -u bench.py --no-mixed --no-shapes --no-cpu ${BENCH_ARGS:-} > gpurun_out/ab_one.log 2>&1; rc=$?
-  [ $rc -eq 0 ] || { echo "variant '$v' rc=$rc"; tail -5 gpurun_out/ab_one.log; exit $rc; }
+  env $ev QPB_WAVE_OPTS="$o" timeout -k 10 300 python -u bench.py --full --no-mixed --no-shapes --no-cpu ${BENCH_ARGS:-} > $TMPDIR/ab_one.log 2>&1; rc=$?
+  [ $rc -eq 0 ] || { echo "variant '$v' rc=$rc"; tail -5 $TMPDIR/ab_one.log; exit $rc; }
   python3 -c "
-import json,sys
-r=[json.loads(l) for l in open('gpurun_out/ab_one.log') if l.startswith('{')][-1]
+import json,os,sys
+r=[json.loads(l) for l in open(os.environ['TMPDIR']+'/ab_one.log') if l.startswith('{')][-1]
 lb=r.get('large_batch') or {}
 print(json.dumps({'variant': sys.argv[1], 'rep': int(sys.argv[2]), 'value': r['value'], 'kernel_ms': r['roofline']['kernel_ms'], 'large_kernel_ms': lb.get('kernel_ms'), 'large_value': lb.get('value')}))" "$v" "$rep" | tee -a gpurun_out/ab.jsonl
 done; done

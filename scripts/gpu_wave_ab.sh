@@ -12,7 +12,7 @@ for rep in 1 2; do for v in "${VS[@]}"; do
   o="$v"; [ "$o" = "-" ] && o=""; tag=$(echo "${v:-def}" | tr -c 'A-Za-z0-9=\n' '_')
   QPB_WAVE_OPTS="$o" timeout -k 10 300 python -u scripts/wave_timing.py c30:amd c30 > $out/t_${tag}_$rep.jsonl 2>> $out/err.log; rc=$?; fatal $rc timing; [ $rc = 0 ] || exit $rc
   QPB_WAVE_OPTS="$o" timeout -k 10 200 python -u scripts/dropin_latency.py --shape c30 --mode fast > $out/lat_${tag}_$rep.json 2>> $out/err.log; rc=$?; fatal $rc lat; [ $rc = 0 ] || exit $rc
-  QPB_WAVE_OPTS="$o" timeout -k 10 400 python -u bench.py --no-cpu --no-mixed --steps 100 --warmup 10 > $out/b_${tag}_$rep.log 2>> $out/err.log; rc=$?; fatal $rc bench; [ $rc = 0 ] || exit $rc
+  QPB_WAVE_OPTS="$o" timeout -k 10 400 python -u bench.py --full --no-cpu --no-mixed --steps 100 --warmup 10 > $out/b_${tag}_$rep.log 2>> $out/err.log; rc=$?; fatal $rc bench; [ $rc = 0 ] || exit $rc
   python3 - "$out" "$tag" "$rep" <<'PY'
 import json, sys
 out, tag, rep = sys.argv[1:]

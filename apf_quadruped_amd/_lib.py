@@ -85,6 +85,9 @@ def lib() -> C.CDLL:
     L.qpb_argmin_allgather.argtypes = [vp, vp, C.c_long, C.c_long, C.c_long, vp, vp, vp]
     L.qpb_argmin_reduce.argtypes = [vp, C.c_long, C.c_long, vp, vp]
     L.qpb_assemble_controller.argtypes = [vp, C.c_long, vp, C.c_int, vp, C.c_double] + [vp] * 8
+    L.qpb_assemble_gait.restype = C.c_int
+    L.qpb_assemble_gait.argtypes = ([vp, C.c_long, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_double, C.c_int]
+                                    + [vp] * 8)
     L.qpb_apf_wrench.argtypes = [C.c_long, C.POINTER(QpbApfState), vp, vp, vp, vp]
     L.qpb_apf_update.argtypes = [C.POINTER(QpbApfState), dp, C.c_double, dp]
     L.qpb_amd_order.restype = C.c_int

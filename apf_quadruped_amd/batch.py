@@ -288,6 +288,46 @@ class Plan:
                                                   C.c_void_p(stream.cuda_stream)), "qpb_assemble_controller")
         return out
 
+    def assemble_gait(self, terms, stance, swing=None, B=None, shared=False, swing_shared=False, wdes=None, mu=0.5,
+                      trot_b_dynamics=False, out=None, check=None, stream=None):
+        """On-device assembly of the controller's QP for any stance set of its gait
+        (qpb_assemble_gait): stance = bitmask of the feet in contact (bit i = foot i,
+        BR BL FL FR) -- 0xF stance 30/68/18 (exactly assemble_controller), 0xA / 0x5
+        trot 30/70/12, 0xE / 0xB / 0xD / 0x7 crawl 30/69/15.  terms, shared, wdes, mu,
+        check as assemble_controller; swing = float64 device tensor of the swing-foot
+        task (tiled, nv = workloads.SWING_NV; or one shared copy with
+        swing_shared=True; not needed for 0xF); trot_b_dynamics: write the crawl
+        formula of b for trot too instead of the source's zero.  Returns the dict of
+        the plan's tiled inputs P, A, G, c, h, b."""
+        import torch
+        if B is None:
+            if not shared:
+                B = terms.numel() // 480
+            elif wdes is not None:
+                B = wdes.numel() // 6
+            elif swing is not None and not swing_shared:
+                B = swing.numel() // 36
+            else:
+                B = 1
+        B = int(B)
+        T = ntiles(B) * TILE
+        dev = terms.device
+        if out is None:
+            f = dict(dtype=torch.float64, device=dev)
+            out = dict(P=torch.empty(self.info.nnzP * T, **f), A=torch.empty(self.info.nnzA * T, **f),
+                       G=torch.empty(self.info.nnzG * T, **f), c=torch.empty(self.n * T, **f),
+                       h=torch.empty(self.m * T, **f), b=torch.empty(self.p * T, **f))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+        flags = 0x1 if trot_b_dynamics else 0           # QPB_GAIT_TROT_B_DYNAMICS
+        check_(_lib.lib().qpb_assemble_gait(self._h, B, int(stance), ptr(terms), int(bool(shared)), ptr(wdes),
+                                            ptr(swing), int(bool(swing_shared)), float(mu), flags,
+                                            ptr(out["P"]), ptr(out["A"]), ptr(out["G"]), ptr(out["c"]),
+                                            ptr(out["h"]), ptr(out["b"]), ptr(check),
+                                            C.c_void_p(stream.cuda_stream)), "qpb_assemble_gait")
+        return out
+
     def unpack(self, out, B):
         """Device tiled outputs -> dict of host numpy arrays [B, n] etc."""
         r = dict(x=from_tiled(out["x"], B, self.n).cpu().numpy(),

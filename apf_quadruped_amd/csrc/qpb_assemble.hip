@@ -314,11 +314,12 @@ __global__ void __launch_bounds__(256) qpb_fill_int_k(int *p, long n, int v) {
     if (i < n) p[i] = v;
 }
 
-// entries of the controller stance QP for this plan (see CtlArgs); empty if the
-// plan's shape is not 30/68/18
-std::vector<int> controller_entries(const qpb::Plan &pl) {
+// entries of a 30-variable controller QP for this plan (see CtlArgs): every
+// position of P (its stored triangle), A and G with the plan's CSC slot or -1,
+// then the rows of c, h and b
+std::vector<int> qp_entries(const qpb::Plan &pl) {
     std::vector<int> ent;
-    if (pl.n != 30 || pl.m != 68 || pl.p != 18) return ent;
+    const int m = (int)pl.m, p = (int)pl.p;
     auto slot_of = [](const qpb::Pattern &pt, int i, int j) {
         for (long k = pt.jc[j]; k < pt.jc[j + 1]; k++)
             if (pt.ir[k] == i) return (int)k;
@@ -332,13 +333,170 @@ std::vector<int> controller_entries(const qpb::Plan &pl) {
             ent.push_back(slot_of(pl.Pin, i, j));
         }
     for (int j = 0; j < 30; j++)
-        for (int i = 0; i < 18; i++) { ent.push_back(M_A << 16 | i << 8 | j); ent.push_back(slot_of(pl.A, i, j)); }
+        for (int i = 0; i < p; i++) { ent.push_back(M_A << 16 | i << 8 | j); ent.push_back(slot_of(pl.A, i, j)); }
     for (int j = 0; j < 30; j++)
-        for (int i = 0; i < 68; i++) { ent.push_back(M_G << 16 | i << 8 | j); ent.push_back(slot_of(pl.G, i, j)); }
+        for (int i = 0; i < m; i++) { ent.push_back(M_G << 16 | i << 8 | j); ent.push_back(slot_of(pl.G, i, j)); }
     for (int i = 0; i < 30; i++) { ent.push_back(M_C << 16 | i << 8); ent.push_back(i); }
-    for (int i = 0; i < 68; i++) { ent.push_back(M_H << 16 | i << 8); ent.push_back(i); }
-    for (int i = 0; i < 18; i++) { ent.push_back(M_B << 16 | i << 8); ent.push_back(i); }
+    for (int i = 0; i < m; i++) { ent.push_back(M_H << 16 | i << 8); ent.push_back(i); }
+    for (int i = 0; i < p; i++) { ent.push_back(M_B << 16 | i << 8); ent.push_back(i); }
     return ent;
+}
+
+// entries of the controller stance QP; empty if the plan's shape is not 30/68/18
+std::vector<int> controller_entries(const qpb::Plan &pl) {
+    if (pl.n != 30 || pl.m != 68 || pl.p != 18) return {};
+    return qp_entries(pl);
+}
+
+// ---------------------------------------------------------------------------
+// The controller's swing-phase QPs from the same robot terms plus the swing-foot
+// task: trot 30/70/12 (main.cpp:1730-2005, :2486-2695) and crawl 30/69/15
+// (main.cpp:2915-3232); numpy restatement: workloads.controller_gait_qp_from_terms.
+// With k stance feet, nw = 12 - 3k, x = [ddx 6; ddq 12; f_st 3k; slack nw], the
+// stance / swing feet each in ascending foot order, o_s = 18 + 3k:
+//   Q = 50 T_s' T_s + R, T_s = Jst_c' Sigma, R = I, slack diagonal w_slack
+//   c = -T_s' (50 I)' Wcom_des
+//   A = [M_com 0 -Jst_c' 0; Jst_c Jst_q 0 0]   b = [-BiasCOM(0:6); -Jdqd_st] (or 0: trot)
+//   D = friction (5k) | [0 M_jj -Jst_q' 0] | -(same) | [Jsw_c Jsw_q 0 -I]
+//       | [-Jsw_c -Jsw_q 0 -I] | [0 I] | [0 -I]
+//   C = 0 | 60 - bias_j | -(-60 - bias_j) | v - Jdqd_sw | -(v - Jdqd_sw) | ddq_max | -ddq_min
+//       v = (acc + 20 vel_delta) + 300 pos_delta
+// One kernel for every stance set: the foot lists travel in the argument struct.
+struct GaitArgs {
+    const double *terms;
+    long tstride;          // 0: one shared copy; 1: tiled SoA (nv = T_NV)
+    const double *wdes;    // tiled nv = 6 or NULL (terms' wdes)
+    const double *swing;   // acc[12] pos_delta[12] vel_delta[12], foot-major
+    long sstride;          // 0: one shared copy; 1: tiled SoA (nv = S_NV)
+    const int *ent;        // pairs {code = mat << 16 | row << 8 | col, slot}
+    int nent, nP, nA, nG;
+    int k, nw, m, p;       // stance feet, slack count 12 - 3k, plan rows
+    unsigned st, sw;       // byte f: first Jst row (3 foot) of the f-th stance / swing foot
+    int b_zero;            // b identically 0 (the trot source never stores Jdqdst)
+    double mu, w_slack;
+    double *P, *A, *G, *c, *h, *b;
+    int *check;
+    long B;
+};
+
+enum : int { S_ACC = 0, S_POS = 12, S_VEL = 24, S_NV = 36 };
+
+#pragma clang fp contract(off)
+struct GaitQP {
+    const GaitArgs &a;
+    long tile;
+    int ql;
+    __device__ double T(int i) const {
+        return a.tstride ? a.terms[tile * (T_NV * 64) + (long)i * 64 + ql] : a.terms[i];
+    }
+    __device__ double S(int i) const {
+        return a.sstride ? a.swing[tile * (S_NV * 64) + (long)i * 64 + ql] : a.swing[i];
+    }
+    __device__ double W(int k) const { return a.wdes ? a.wdes[tile * (6 * 64) + k * 64 + ql] : T(T_WDES + k); }
+    __device__ double J(int r, int col) const { return T(T_JST + r * 18 + col); }   // Jst(r, col), all four feet
+    // Jst row of stance-force / swing-task coordinate u (wave-uniform)
+    __device__ int fr(int u) const { const int f = u / 3; return (int)((a.st >> (8 * f)) & 255u) + (u - 3 * f); }
+    __device__ int sr(int u) const { const int f = u / 3; return (int)((a.sw >> (8 * f)) & 255u) + (u - 3 * f); }
+    __device__ double value(int mat, int i, int j) const {
+        const int o_s = 18 + 3 * a.k, r0 = 5 * a.k, r1 = r0 + 24, r2 = r1 + 2 * a.nw;
+        switch (mat) {
+        case M_P: {
+            if (i >= 18 && j >= 18 && i < o_s && j < o_s) {
+                const int ri = fr(i - 18), rj = fr(j - 18);
+                double d = 0.0;
+                for (int k = 0; k < 6; k++) d = d + J(ri, k) * J(rj, k);
+                return 50.0 * d + (i == j ? 1.0 : 0.0);
+            }
+            if (i != j) return 0.0;
+            return i >= o_s ? a.w_slack : 1.0;
+        }
+        case M_A:
+            if (i < 6) {
+                if (j < 6) return T(T_MCOM + 6 * i + j);
+                return (j >= 18 && j < o_s) ? -J(fr(j - 18), i) : 0.0;
+            }
+            return j < 18 ? J(fr(i - 6), j) : 0.0;
+        case M_G: {
+            if (i < r0) {
+                const int blk = i / 5, t = i - 5 * blk, jj = j - 18 - 3 * blk;
+                if (jj < 0 || jj > 2) return 0.0;
+                // cfr (main.cpp:1897-1901, :3093-3097)
+                if (jj == 2) return t == 4 ? -1.0 : -a.mu;
+                if (jj == 0) return t == 0 ? 1.0 : (t == 2 ? -1.0 : 0.0);
+                return t == 1 ? 1.0 : (t == 3 ? -1.0 : 0.0);
+            }
+            if (i < r1) {
+                const double sg = i < r0 + 12 ? 1.0 : -1.0;
+                const int l = i < r0 + 12 ? i - r0 : i - r0 - 12;
+                if (j >= 6 && j < 18) return sg * T(T_MJJ + 12 * l + (j - 6));
+                if (j >= 18 && j < o_s) return -sg * J(fr(j - 18), 6 + l);
+                return 0.0;
+            }
+            if (i < r2) {
+                const bool neg = i >= r1 + a.nw;
+                const int u = neg ? i - r1 - a.nw : i - r1;
+                if (j < 18) {
+                    const double v = J(sr(u), j);
+                    return neg ? -v : v;
+                }
+                return j == o_s + u ? -1.0 : 0.0;
+            }
+            const int l = i < r2 + 12 ? i - r2 : i - r2 - 12;
+            return j == 6 + l ? (i < r2 + 12 ? 1.0 : -1.0) : 0.0;
+        }
+        case M_C: {
+            if (i < 18 || i >= o_s) return 0.0;
+            const int ri = fr(i - 18);
+            double d = 0.0;
+            for (int k = 0; k < 6; k++) d = d + J(ri, k) * W(k);
+            return -50.0 * d;
+        }
+        case M_H: {
+            if (i < r0) return 0.0;
+            if (i < r0 + 12) return 60.0 - T(T_BIAS + 6 + (i - r0));
+            if (i < r1) return -(-60.0 - T(T_BIAS + 6 + (i - r0 - 12)));
+            if (i < r2) {
+                const bool neg = i >= r1 + a.nw;
+                const int r = sr(neg ? i - r1 - a.nw : i - r1);
+                // vdotswdes = accdes + Kd veldelta + Kp posdelta (main.cpp:1988, :3228)
+                const double v = (S(S_ACC + r) + 20.0 * S(S_VEL + r)) + 300.0 * S(S_POS + r);
+                const double d = v - T(T_JDQD + r);
+                return neg ? -d : d;
+            }
+            const double dt = 0.025, k2 = 2.0 / (dt * dt);
+            const bool mx = i < r2 + 12;
+            const int l = mx ? i - r2 : i - r2 - 12;
+            const double lim = mx ? T(T_QMAX + l) : T(T_QMIN + l);
+            const double v = k2 * ((lim - T(T_Q + l)) - dt * T(T_DQ + l));
+            return mx ? v : -v;
+        }
+        default:
+            if (a.b_zero) return 0.0;
+            return i < 6 ? -T(T_BIAS + i) : -T(T_JDQD + fr(i - 6));
+        }
+    }
+};
+#pragma clang fp contract(on)
+
+// as qpb_assemble_controller_k: one block per 64-QP tile x entry chunk, lane = QP,
+// one wave per table entry at a time, every store a coalesced row
+__global__ void __launch_bounds__(256) qpb_assemble_gait_k(GaitArgs a) {
+    const long tile = blockIdx.x;
+    const int ql = threadIdx.x & 63, g = threadIdx.x >> 6;
+    if (tile * 64 + ql >= a.B) return;
+    const GaitQP qp{a, tile, ql};
+    bool ok = true;
+    for (int e = blockIdx.y * 4 + g; e < a.nent; e += gridDim.y * 4) {
+        const int code = a.ent[2 * e], slot = a.ent[2 * e + 1];
+        const int mat = code >> 16, i = (code >> 8) & 255, j = code & 255;
+        const double v = qp.value(mat, i, j);
+        if (slot < 0) { ok = ok && v == 0.0; continue; }
+        double *dst = mat == M_P ? a.P + tile * ((long)a.nP * 64) : mat == M_A ? a.A + tile * ((long)a.nA * 64)
+                    : mat == M_G ? a.G + tile * ((long)a.nG * 64) : mat == M_C ? a.c + tile * (30 * 64)
+                    : mat == M_H ? a.h + tile * ((long)a.m * 64) : a.b + tile * ((long)a.p * 64);
+        dst[(long)slot * 64 + ql] = v;
+    }
+    if (!ok && a.check) a.check[tile * 64 + ql] = 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -461,6 +619,89 @@ extern "C" int qpb_assemble_controller(const qpb_plan *plan_c, long B, const dou
                            B, 1);
     const unsigned tiles = (unsigned)((B + 63) / 64);
     hipLaunchKernelGGL(qpb_assemble_controller_k, dim3(tiles, 8), dim3(256), 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return qpb::set_error(QPB_EHIP, (std::string("assemble: ") + hipGetErrorString(e)).c_str());
+    return QPB_OK;
+}
+
+extern "C" int qpb_assemble_gait(const qpb_plan *plan_c, long B, int stance, const double *terms, int terms_shared,
+                                 const double *wdes, const double *swing, int swing_shared, double mu, int flags,
+                                 double *P, double *A, double *G, double *c, double *h, double *b, int *check,
+                                 void *stream) {
+    qpb_plan *plan = const_cast<qpb_plan *>(plan_c);
+    if (!plan) return qpb::set_error(QPB_EINVAL, "NULL plan");
+    // the stance sets the controller uses: all feet, the diagonal pairs, any three
+    int k = 0;
+    for (int i = 0; i < 4; i++) k += (stance >> i) & 1;
+    if (stance < 0 || stance > 0xF || k < 2 || (k == 2 && stance != 0xA && stance != 0x5))
+        return qpb::set_error(QPB_EINVAL, "stance: 0xF, a diagonal pair (0xA, 0x5) or three feet");
+    if (flags & ~QPB_GAIT_TROT_B_DYNAMICS) return qpb::set_error(QPB_EINVAL, "unknown flags");
+    const qpb::Plan &pl = plan->pl;
+    const int nw = 12 - 3 * k, m = 5 * k + 48 + 2 * nw, p = 6 + 3 * k;
+    if (pl.n != 30 || pl.m != m || pl.p != p)
+        return qpb::set_error(QPB_ESHAPE, k == 4   ? "plan is not a 30/68/18 controller stance QP"
+                                          : k == 2 ? "plan is not a 30/70/12 controller trot QP"
+                                                   : "plan is not a 30/69/15 controller crawl QP");
+    if (B < 0) return qpb::set_error(QPB_EINVAL, "need B >= 0");
+    if (B == 0) return QPB_OK;
+    if (!terms || !P || !A || !G || !c || !h || !b || (k < 4 && !swing))
+        return qpb::set_error(QPB_EINVAL, "NULL data pointer");
+    if (k == 4) return qpb_assemble_controller(plan_c, B, terms, terms_shared, wdes, mu, P, A, G, c, h, b, check, stream);
+    // the entry table of (plan, stance) -- host, then per device -- is built once,
+    // under a lock: concurrent callers on one plan must not build or upload it twice
+    void *tab = nullptr;
+    size_t nent = 0;
+    {
+        static std::mutex mtx;
+        std::lock_guard<std::mutex> lk(mtx);
+        std::vector<int> &table = plan->gait_table[stance];
+        if (table.empty()) table = qp_entries(pl);
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return qpb::set_error(QPB_EHIP, "hipGetDevice failed (no GPU?)");
+        nent = table.size();
+        auto it = plan->gait_dev.find({stance, dev});
+        if (it != plan->gait_dev.end()) tab = it->second;
+        else {
+            const size_t bytes = nent * sizeof(int);
+            if (hipMalloc(&tab, bytes) != hipSuccess) return qpb::set_error(QPB_ENOMEM, "assembly table");
+            if (hipMemcpy(tab, table.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipFree(tab);     // nothing half-uploaded stays in the cache
+                return qpb::set_error(QPB_EHIP, "assembly table upload");
+            }
+            plan->gait_dev[{stance, dev}] = tab;
+        }
+    }
+    GaitArgs a{};
+    a.terms = terms;
+    a.tstride = terms_shared ? 0L : 1L;
+    a.wdes = wdes;
+    a.swing = swing;
+    a.sstride = swing_shared ? 0L : 1L;
+    a.ent = (const int *)tab;
+    a.nent = (int)(nent / 2);
+    a.nP = (int)pl.Pin.nnz();
+    a.nA = (int)pl.A.nnz();
+    a.nG = (int)pl.G.nnz();
+    a.k = k;
+    a.nw = nw;
+    a.m = m;
+    a.p = p;
+    for (int i = 0, ns = 0, nsw = 0; i < 4; i++) {
+        if ((stance >> i) & 1) a.st |= (unsigned)(3 * i) << (8 * ns++);
+        else a.sw |= (unsigned)(3 * i) << (8 * nsw++);
+    }
+    a.b_zero = (k == 2 && !(flags & QPB_GAIT_TROT_B_DYNAMICS)) ? 1 : 0;
+    a.mu = mu;
+    a.w_slack = k == 2 ? 1e8 : 1e4;      // main.cpp:1751, :2976
+    a.P = P; a.A = A; a.G = G; a.c = c; a.h = h; a.b = b;
+    a.check = check;
+    a.B = B;
+    (void)hipGetLastError();   // a stale error of an earlier API call is not these launches'
+    if (check)
+        hipLaunchKernelGGL(qpb_fill_int_k, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, check,
+                           B, 1);
+    const unsigned tiles = (unsigned)((B + 63) / 64);
+    hipLaunchKernelGGL(qpb_assemble_gait_k, dim3(tiles, 8), dim3(256), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qpb::set_error(QPB_EHIP, (std::string("assemble: ") + hipGetErrorString(e)).c_str());
     return QPB_OK;

@@ -167,6 +167,13 @@ qpb_plan::~qpb_plan() {
             (void)hipSetDevice(cur);
         }
     }
+    for (auto &kv : gait_dev) {
+        int cur = 0;
+        if (hipGetDevice(&cur) == hipSuccess && hipSetDevice(kv.first.second) == hipSuccess) {
+            (void)hipFree(kv.second);
+            (void)hipSetDevice(cur);
+        }
+    }
     for (auto *m : {&tree_dev, &tree2_dev})
         for (auto &kv : *m) {
             int cur = 0;

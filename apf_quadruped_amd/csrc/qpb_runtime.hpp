@@ -5,6 +5,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "qpb_codegen.hpp"
@@ -57,6 +58,10 @@ struct qpb_plan {
     std::map<std::string, std::shared_ptr<std::vector<char>>> warm_code;
     std::vector<int> ctl_table;                 // controller-QP assembly entries (qpb_assemble_controller)
     std::map<int, void *> ctl_dev;              // device -> uploaded entries
+    // gait assembly (qpb_assemble_gait, trot / crawl): stance mask -> entries, and
+    // (stance mask, device) -> uploaded entries
+    std::map<int, std::vector<int>> gait_table;
+    std::map<std::pair<int, int>, void *> gait_dev;
     ~qpb_plan();
 };
 

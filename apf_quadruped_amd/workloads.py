@@ -445,6 +445,150 @@ def controller_qp(seed: int, qp_ids, phase: str = "stance"):
     return controller_qp_from_terms(controller_terms(seed, qp_ids))
 
 
+# The swing-foot task of qpb_assemble_gait (include/qpswift_hip.h), per QP: the
+# planner's foot acceleration accdes, posdelta = planned - measured foot position and
+# veldelta likewise (main.cpp:1944-1981, :3147-3222), each for all four feet in
+# BR BL FL FR order, x y z per foot; entries of stance feet are ignored.
+SWING_TERMS = (("sw_acc", 12), ("sw_pos", 12), ("sw_vel", 12))
+SWING_NV = sum(k for _, k in SWING_TERMS)
+
+# stance masks of the controller's gait (bit i = foot i, BR BL FL FR) -> phase
+GAIT_PHASES = {0xF: "stance",
+               0xA: "trot", 0x5: "trot",                                   # BL+FR :1730-1733, BR+FL :2486-2489
+               0xE: "crawl", 0xB: "crawl", 0xD: "crawl", 0x7: "crawl"}     # swingleg 0 (BR), 1 (FL), 2 (BL), 3 (FR)
+GAIT_SLACK_WEIGHT = {"trot": 1e8, "crawl": 1e4}                            # main.cpp:1751, :2976
+
+
+def pack_swing(t: dict) -> np.ndarray:
+    """terms dict -> [B, SWING_NV] rows in the SWING_TERMS layout."""
+    B = np.asarray(t["sw_acc"]).shape[0]
+    return np.concatenate([np.asarray(t[k], np.float64).reshape(B, -1) for k, _ in SWING_TERMS], 1)
+
+
+def _gait_feet(stance: int):
+    """Stance mask -> (stance feet, swing feet), each ascending (stl1 < stl2 < stl3,
+    swl1 < swl2 in main.cpp)."""
+    if stance not in GAIT_PHASES:
+        raise ValueError(f"stance mask {stance!r}: not a stance set of the controller's gait")
+    st = tuple(i for i in range(4) if (stance >> i) & 1)
+    return st, tuple(i for i in range(4) if i not in st)
+
+
+def _foot_rows(feet):
+    return np.array([3 * i + a for i in feet for a in range(3)], dtype=np.int64)
+
+
+def controller_gait_qp_from_terms(t: dict, stance: int, mu: float = MU, trot_b_dynamics: bool = False):
+    """The controller's QP for the stance set `stance` from its robot terms plus the
+    swing-foot task (the numpy reference of qpb_assemble_gait): 0xF is exactly
+    controller_qp_from_terms; the diagonal pairs restate the trot QP 30/70/12
+    (main.cpp:1730-2005 for BL+FR, :2486-2695 for BR+FL); three feet restate the crawl
+    QP 30/69/15 (qpproblemcrawl, main.cpp:2915-3232).  With k stance feet and
+    x = [ddx 6; ddq 12; f_st 3k; slack 12-3k]:
+      Q = 50 T_s' T_s + R, T_s = Jst_c' Sigma; R = I with 1e8 (trot, :1751) or 1e4
+          (crawl, :2976) on the slack diagonal;  c = -T_s' (50 I)' W
+      A = [M_com 0 -Jst_c' 0; Jst_c Jst_q 0 0]                  (:1844-1848, :3021-3029)
+      b = [-BiasCOM(0:6); -Jdqd_st] for crawl (:3042-3044); 0 for trot, whose Jdqdst
+          is computed and never stored (:1851-1854, :2557) -- trot_b_dynamics writes
+          the crawl formula for trot too (it has no effect on the other phases)
+      D = friction | [0 M_jj -Jst_q' 0] | -(same) | [Jsw_c Jsw_q 0 -I]
+          | [-Jsw_c -Jsw_q 0 -I] | [0 I] | [0 -I]                (:1857-1911, :3048-3107)
+      C = 0 | 60 - bias_j | -(-60 - bias_j) | v - Jdqd_sw | -v + Jdqd_sw | ddq_max | -ddq_min,
+          v = accdes + 20 veldelta + 300 posdelta                (:1915-1992, :3110-3230)"""
+    st, sw = _gait_feet(stance)
+    if not sw:
+        return controller_qp_from_terms(t, mu)
+    phase = GAIT_PHASES[stance]
+    Jall, Mcom, Mjj = (np.asarray(t[k], np.float64) for k in ("Jst", "Mcom", "Mjj"))
+    B = Jall.shape[0]
+    rs, rw = _foot_rows(st), _foot_rows(sw)
+    ns, nw = len(rs), len(rw)
+    n, m, p = 30, 5 * len(st) + 24 + 2 * nw + 24, 6 + ns
+    o_s = 18 + ns
+    Jst_c, Jst_q = Jall[:, rs, 0:6], Jall[:, rs, 6:18]
+    Jsw = Jall[:, rw, :]
+    Ts = np.zeros((B, 6, n))
+    Ts[:, :, 18:o_s] = np.transpose(Jst_c, (0, 2, 1))
+    R = np.eye(n)
+    R[np.arange(o_s, n), np.arange(o_s, n)] = GAIT_SLACK_WEIGHT[phase]
+    P = 50.0 * np.einsum("bki,bkj->bij", Ts, Ts) + R[None]
+    c = -50.0 * np.einsum("bki,bk->bi", Ts, np.asarray(t["wdes"], np.float64))
+    A = np.zeros((B, p, n))
+    A[:, 0:6, 0:6] = Mcom
+    A[:, 0:6, 18:o_s] = -np.transpose(Jst_c, (0, 2, 1))
+    A[:, 6:, 0:6] = Jst_c
+    A[:, 6:, 6:18] = Jst_q
+    bias = np.asarray(t["bias"], np.float64)
+    jdqd = np.asarray(t["jdqd"], np.float64)
+    if phase == "trot" and not trot_b_dynamics:
+        b = np.zeros((B, p))
+    else:
+        b = np.concatenate([-bias[:, 0:6], -jdqd[:, rs]], 1)
+    G = np.zeros((B, m, n))
+    h = np.zeros((B, m))
+    cfr = friction_block(mu)
+    for i in range(len(st)):
+        G[:, 5 * i:5 * i + 5, 18 + 3 * i:18 + 3 * i + 3] = cfr
+    r0 = 5 * len(st)
+    JqT = np.transpose(Jst_q, (0, 2, 1))
+    G[:, r0:r0 + 12, 6:18] = Mjj
+    G[:, r0:r0 + 12, 18:o_s] = -JqT
+    G[:, r0 + 12:r0 + 24, 6:18] = -Mjj
+    G[:, r0 + 12:r0 + 24, 18:o_s] = JqT
+    bias_j = bias[:, 6:18]
+    h[:, r0:r0 + 12] = 60.0 - bias_j
+    h[:, r0 + 12:r0 + 24] = -(-60.0 - bias_j)
+    r1 = r0 + 24
+    G[:, r1:r1 + nw, 0:18] = Jsw
+    G[:, r1:r1 + nw, o_s:n] = -np.eye(nw)[None]
+    G[:, r1 + nw:r1 + 2 * nw, 0:18] = -Jsw
+    G[:, r1 + nw:r1 + 2 * nw, o_s:n] = -np.eye(nw)[None]
+    acc, pos, vel = (np.asarray(t[k], np.float64)[:, rw] for k in ("sw_acc", "sw_pos", "sw_vel"))
+    v = (acc + 20.0 * vel) + 300.0 * pos
+    h[:, r1:r1 + nw] = v - jdqd[:, rw]
+    h[:, r1 + nw:r1 + 2 * nw] = -v + jdqd[:, rw]
+    r2 = r1 + 2 * nw
+    G[:, r2:r2 + 12, 6:18] = np.eye(12)[None]
+    G[:, r2 + 12:r2 + 24, 6:18] = -np.eye(12)[None]
+    dt = 0.025
+    q, dq = np.asarray(t["q"], np.float64), np.asarray(t["dq"], np.float64)
+    h[:, r2:r2 + 12] = (2 / dt ** 2) * (np.asarray(t["qmax"], np.float64) - q - dt * dq)
+    h[:, r2 + 12:r2 + 24] = -((2 / dt ** 2) * (np.asarray(t["qmin"], np.float64) - q - dt * dq))
+    return dict(n=n, m=m, p=p, P=P, c=c, A=A, b=b, G=G, h=h)
+
+
+def controller_gait_terms(seed: int, qp_ids, stance: int):
+    """Feasible synthetic robot terms for controller_gait_qp_from_terms /
+    qpb_assemble_gait: controller_terms, with BiasCOM(0:6) and the stance rows of
+    JdqdCOM_lin overwritten so that the crawl-formula right-hand side
+    b = -[BiasCOM(0:6); Jdqd_st] is consistent with a state (ddx*, ddq*, f*) drawn
+    from a separate stream, f* inside the friction pyramids of the stance feet; the
+    swing rows of Jdqd are free in +-0.1, and the swing-foot task is sw_acc in +-2,
+    sw_pos in +-0.02, sw_vel in +-0.2 (SWING_TERMS)."""
+    st, sw = _gait_feet(stance)
+    qp_ids = np.atleast_1d(np.asarray(qp_ids, dtype=np.int64))
+    B = len(qp_ids)
+    t = controller_terms(seed, qp_ids)
+    u = uniforms(seed ^ 0x6A17, qp_ids, 6 + 12 + 12 + 12 + SWING_NV)
+    ddx = 2.0 * u[:, 0:6] - 1.0
+    ddq = 2.0 * u[:, 6:18] - 1.0
+    uf = u[:, 18:30].reshape(B, 4, 3)
+    fz = 40.0 + 60.0 * uf[..., 2]
+    f = np.stack([(0.8 * uf[..., 0] - 0.4) * MU * fz, (0.8 * uf[..., 1] - 0.4) * MU * fz, fz], -1)
+    rs = _foot_rows(st)
+    f_st = f[:, list(st), :].reshape(B, len(rs))
+    Jst_c, Jst_q = t["Jst"][:, rs, 0:6], t["Jst"][:, rs, 6:18]
+    b_dyn = np.einsum("bij,bj->bi", t["Mcom"], ddx) - np.einsum("bki,bk->bi", Jst_c, f_st)
+    b_kin = np.einsum("bij,bj->bi", Jst_c, ddx) + np.einsum("bij,bj->bi", Jst_q, ddq)
+    bias = t["bias"].copy()
+    bias[:, 0:6] = -b_dyn
+    jdqd = 0.2 * u[:, 30:42] - 0.1
+    jdqd[:, rs] = -b_kin
+    t.update(bias=bias, jdqd=jdqd, sw_acc=4.0 * u[:, 42:54] - 2.0, sw_pos=0.04 * u[:, 54:66] - 0.02,
+             sw_vel=0.4 * u[:, 66:78] - 0.2)
+    return t
+
+
 def _apf_state_draw(seed: int, rep_field: bool, min_exit: bool) -> dict:
     """One random APF tick state (the fields of qpb_apf_state): stance feet around
     the CoM with jitter, small CoM motion, the controller's nominal versors

@@ -220,6 +220,42 @@ int  qpb_assemble_controller(const qpb_plan *plan, long B, const double *terms, 
                              const double *wdes, double mu, double *P, double *A, double *G,
                              double *c, double *h, double *b, int *check, void *stream);
 
+/* On-device assembly of the controller's QP for any stance set of its gait (SURVEY
+ * §8f row 3): the stance QP above, the trot QP 30/70/12 (main.cpp:1730-2005,
+ * :2486-2695) and the crawl QP 30/69/15 (main.cpp:2915-3232), from the same robot
+ * terms plus the swing-foot task.  stance = bitmask of the feet in contact (bit i =
+ * foot i; BR, BL, FL, FR as in qpb_assemble_contact):
+ *   0xF                     stance  30/68/18  exactly qpb_assemble_controller (swing may be NULL)
+ *   0xA (BL+FR), 0x5 (BR+FL) trot   30/70/12
+ *   0xE, 0xB, 0xD, 0x7      crawl   30/69/15  (swing foot BR, FL, BL, FR: swingleg 0..3)
+ * any other mask: QPB_EINVAL.  terms, terms_shared, wdes, mu, check and the outputs
+ * are those of qpb_assemble_controller; Jst and jdqd always hold all four feet, the
+ * call selects their rows.  swing: QPB_SWING_NV doubles per QP -- acc[12],
+ * pos_delta[12], vel_delta[12], each foot-major (BR BL FL FR, x y z) -- tiled with
+ * nv = QPB_SWING_NV, or one copy when swing_shared = 1; entries of stance feet are
+ * ignored.  With k stance feet, x = [ddx 6; ddq 12; f_st 3k; slack 12 - 3k], stance
+ * and swing feet each in ascending foot order (stl1 < stl2 < stl3, swl1 < swl2):
+ *   P = 50 T_s' T_s + R,  R = I with the slack diagonal 1e8 (trot, :1751) / 1e4 (crawl, :2976)
+ *   c, A: as the stance QP, over the stance feet
+ *   G = friction (5k rows) | [0 M_jj -Jst_q' 0] | -(same) | [Jsw_c Jsw_q 0 -I]
+ *       | [-Jsw_c -Jsw_q 0 -I] | [0 I] | [0 -I]
+ *   h = 0 | 60 - bias_j | 60 + bias_j | v - Jdqd_sw | -(v - Jdqd_sw) | ddq_max | -ddq_min,
+ *       v = (acc + 20 vel_delta) + 300 pos_delta   (:1983-1992, :3224-3230)
+ *   b = [-BiasCOM(0:6); -Jdqd_st] for crawl (:3042-3044); identically 0 for trot, whose
+ *       source computes Jdqdst and never stores it (:1851-1854, :2557) -- unless flags
+ *       has QPB_GAIT_TROT_B_DYNAMICS, which writes the crawl formula for trot too (no
+ *       effect on the other phases).  Unknown flag bits: QPB_EINVAL.
+ * Checked before any HIP call, in this order: NULL plan (QPB_EINVAL), mask and flags
+ * (QPB_EINVAL), the plan's shape against the mask's phase (QPB_ESHAPE), B == 0
+ * (QPB_OK), NULL data pointers (QPB_EINVAL; swing is required unless stance = 0xF). */
+#define QPB_SWING_NV 36
+#define QPB_GAIT_TROT_B_DYNAMICS 0x1
+int  qpb_assemble_gait(const qpb_plan *plan, long B, int stance,
+                       const double *terms, int terms_shared, const double *wdes,
+                       const double *swing, int swing_shared, double mu, int flags,
+                       double *P, double *A, double *G, double *c, double *h, double *b,
+                       int *check, void *stream);
+
 /* APF-sampled targets (main.cpp:1263-1422) -> the desired CoM wrench each candidate
  * QP tracks (main.cpp:1484-1571).  State of one tick (host struct, shared by all
  * candidates); targets: tiled nv = 2, the candidate target point (x, y) of the
